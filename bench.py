@@ -8,6 +8,7 @@ index is sharded over the ranks and the partial J/K are all-reduced (RCCL): stro
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--nwater 32] [--basis cc-pvtz]
     python bench.py --molecule taxol          # BASELINE config 4 on one GPU: C47H51NO14 def2-TZVP (data/taxol.xyz)
+    python bench.py --dump-outputs DIR        # + what the last timed step returned, as DIR/<name>.npy (see _dump_outputs)
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel: HIP events around every launch of the TIMED steps,
 each on the stream the kernel is launched on (`kernels`); `kernels_serial_pass` is one extra untimed step with J and K on
@@ -28,6 +29,26 @@ sys.path.insert(0, ROOT)
 
 FP64_MFMA_PEAK_TFLOPS = 78.6     # MI355X FP64 matrix peak (vendor spec; 256 CU x 4 SIMD x 32 flop/clk x 2.4 GHz)
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this many bytes of .npy files in all
+
+
+def _dump_outputs(d, arrays):
+    """--dump-outputs DIR: the arrays the timed path returned in its last step, as DIR/<name>.npy in float64, so that two builds
+    can be compared output for output (the inputs are seeded: the same arguments give the same inputs).  When they exceed
+    DUMP_BYTES together, each is replaced by a fixed seeded sample of its flattened elements, the same share of every array
+    (DIR/<name>_sample.npy; the sample depends only on the array's position and size)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = [(n, np.asarray(a, dtype=np.float64)) for n, a in arrays]
+    total = 8 * sum(a.size for _, a in arrays)
+    budget = DUMP_BYTES - 4096 * len(arrays)          # room for the .npy headers
+    written = []
+    for i, (name, a) in enumerate(arrays):
+        if total > budget:
+            idx = np.sort(np.random.RandomState(11 + i).choice(a.size, int(a.size * (budget / float(total))), replace=False))
+            a, name = a.ravel()[idx], name + '_sample'
+        np.save(os.path.join(d, name + '.npy'), a)
+        written.append('%s%s' % (name, list(a.shape)))
+    print('bench.py: last timed step written to %s: %s' % (d, ', '.join(written)), file=sys.stderr)
 
 
 def _aux_label(b):
@@ -127,7 +148,11 @@ def main():
     ap.add_argument('--no-pmc', dest='pmc', action='store_const', const='off')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--pmc-shard', default='', help=argparse.SUPPRESS)      # 'r,w': the child builds and contracts rank r's shard of w only
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last one returned '
+                    '(J and K) to DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded sample of larger outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1 (the timed steps)')
     if args.single_process:
         return single_process_main(args)
     if args.backend:
@@ -296,6 +321,8 @@ def main():
     dt = time.perf_counter() - t0
     comm.set_timer(None)
     dfobj.kernel_timer = None
+    if args.dump_outputs and rank == 0:       # J and K of the last timed step, already summed over the ranks
+        _dump_outputs(args.dump_outputs, [('vj_tril', vjtril.cpu().numpy()), ('vk', vk.cpu().numpy())])
     ksum_live = {k_: (tot_ / args.steps, cnt_ / float(args.steps)) for k_, (tot_, cnt_) in live_timer.summary().items()}
     comm_ms, comm_bytes = ctimer.total_ms() if ctimer.records else (0.0, 0)
     comm_info = {'backend': backend, 'collectives_per_step': len(ctimer.records) / max(args.steps, 1),
@@ -765,6 +792,8 @@ def single_process_main(args):
         vj, vk = obj.get_jk(dm, hermi=1)
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, [('vj', vj), ('vk', vk)])
     ms = dt / args.steps * 1e3
     lay = obj.layout()
     tm = obj.last_timing()                                # of the last timed call: host clocks + HIP events inside the handle

@@ -306,3 +306,18 @@ def test_hdf5_interoperates_with_h5py(tmp_path):
     assert subprocess.run([py, '-c', code]).returncode == 0
     with hdf5.File(theirs) as f:
         assert np.array_equal(f['j3c'].read_rows(0, 12), a * 2)
+
+
+def test_hdf5_reads_a_file_h5py_wrote():
+    """tests/golden/h5py_j3c.h5 was written by h5py 3.3 (HDF5 1.10.6) as `f['j3c'] = a * 2` with `a` as above: lib/hdf5.py reads
+    it without an h5py interpreter at hand."""
+    from pyscf_amd.lib import hdf5
+    if not hdf5.available():
+        pytest.skip('libhdf5 not found')
+    a = np.arange(84.0).reshape(12, 7) / 7
+    path = os.path.join(ROOT, 'tests', 'golden', 'h5py_j3c.h5')
+    assert hdf5.is_hdf5(path)
+    with hdf5.File(path) as f:
+        d = f['j3c']
+        assert d.shape == a.shape
+        assert np.array_equal(d.read_rows(0, 12), a * 2) and np.array_equal(d.read_rows(3, 9), a[3:9] * 2)

@@ -84,6 +84,24 @@ def test_bench_two_rank_line_is_complete():
     assert isinstance(two['host_api_breakdown_ms'], list) and two['host_api_breakdown_ms'] and 'probe' in two['host_api_breakdown_ms'][0]
 
 
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: J (packed lower triangle) and K of the last timed step as .npy files; the same inputs through one rank
+    and through two ranks (sharded + all-reduced) give the same arrays."""
+    import numpy as np
+    one = _run(['--gpus', '1', '--steps', '3', '--no-pmc', '--dump-outputs', str(tmp_path / 'one')])
+    _run(['--gpus', '2', '--backend', 'gloo', '--no-pmc', '--dump-outputs', str(tmp_path / 'two')])
+    assert one['steps'] == 3
+    assert sorted(os.listdir(tmp_path / 'one')) == sorted(os.listdir(tmp_path / 'two')) == ['vj_tril.npy', 'vk.npy']
+    vj, vk = np.load(tmp_path / 'one' / 'vj_tril.npy'), np.load(tmp_path / 'one' / 'vk.npy')
+    nao = vk.shape[-1]
+    assert vj.dtype == vk.dtype == np.float64 and vj.shape == (1, nao * (nao + 1) // 2) and vk.shape == (1, nao, nao)
+    assert np.isfinite(vj).all() and np.isfinite(vk).all() and np.abs(vk).max() > 0
+    assert np.abs(vk[0] - vk[0].T).max() < 1e-10 * np.abs(vk).max()
+    for name, a in (('vj_tril', vj), ('vk', vk)):
+        b = np.load(tmp_path / 'two' / (name + '.npy'))
+        assert b.shape == a.shape and np.abs(b - a).max() < 1e-9 * np.abs(a).max(), name
+
+
 def test_bench_refuses_a_world_size_mismatch():
     env = dict(os.environ, WORLD_SIZE='1', RANK='0')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--nwater', '2'], env=env,
